@@ -20,7 +20,13 @@ step writes a complete proof into a fresh proof stream.
 One process per GPU (torchrun); each rank proves its own independent trace
 (weak scaling, no collective on the data path).  Rank 0 prints one JSON line.
 
-Side measurements (not the metric): at N = 1 the other BASELINE configs (C2 2^22 fwd+inv NTT,
+A plain run sets up, warms up, times `--steps` proofs and prints the line; `--dump-outputs DIR`
+also writes the last timed step's proof bytes to DIR/proof_bytes.npy (the inputs are seeded, so two
+builds can be compared byte for byte).  Everything below runs only with `--full`: the HBM copy probe
+and the dominant kernel alone on the chip (roofline.hbm_copy_*, roofline.standalone), the CPU
+baselines, and the side measurements.
+
+Side measurements (`--full`, not the metric): at N = 1 the other BASELINE configs (C2 2^22 fwd+inv NTT,
 the 2^24 north-star LDE + FRI commit, C4's prove at trace 2^16, C5's 2^27 NTT) and the sharded
 paths on a one-rank RCCL communicator (`c5_dist_world1_ms`, `sharded_prove_world1_ms` with a
 byte check against the single-GPU proof); at N > 1 the same sharded paths over all ranks
@@ -848,15 +854,42 @@ def prove_valu_budget(breakdown, ms_per_step):
                           "measured full/half-rate costs / the SIMD cycles of the wall time"}
 
 
+DUMP_MAX_VALUES = 8 << 20  # float32 values per dumped array (32 MiB), well inside the 64 MB a dump may take
+
+
+def dump_outputs(out_dir: str, proof: bytes, rank: int, world: int) -> None:
+    """--dump-outputs: what the last timed step returned to its caller, i.e. the serialized proof
+    (Stark::prove's return value, stark.rs:562), one float32 value per byte, as
+    `proof_bytes.npy`, and its length as `proof_len.npy` (float64).  A proof longer than DUMP_MAX_VALUES
+    is written as a fixed, seeded sample of its bytes (sorted positions, the same in every run).
+    With more than one rank every rank writes its own proof (`proof_bytes_rank<r>.npy`)."""
+    os.makedirs(out_dir, exist_ok=True)
+    suffix = f"_rank{rank}" if world > 1 else ""
+    raw = np.frombuffer(proof, dtype=np.uint8)
+    if raw.size > DUMP_MAX_VALUES:
+        pick = np.sort(np.random.default_rng(20).choice(raw.size, DUMP_MAX_VALUES, replace=False))
+        raw = raw[pick]
+    np.save(os.path.join(out_dir, f"proof_bytes{suffix}.npy"), raw.astype(np.float32))
+    np.save(os.path.join(out_dir, f"proof_len{suffix}.npy"), np.array([len(proof)], dtype=np.float64))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=5)
+    ap.add_argument("--steps", type=int, default=5, help="timed steps (>= 1)")
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--log-trace", type=int, default=LOG_TRACE, help="log2 of the randomized trace rows + 1")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-side", action="store_true", help="skip the side measurements (C2, C4, C5, block, 2^24)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline: the HBM copy probe and the dominant kernel alone on the chip, the side "
+                         "measurements (C2, C4, C5, block, 2^24, RPSSS, sharded paths) and the CPU baselines")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's proof to DIR/proof_bytes.npy (float32, one value per byte)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baselines")
+    ap.add_argument("--no-side", action="store_true",
+                    help="with --full: skip the side measurements (C2, C4, C5, block, 2^24)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -910,6 +943,8 @@ def main():
     elapsed = allreduce_max(t1 - t0, device)
     ms_per_step = elapsed / args.steps * 1e3
     total_elems = wl.elements_per_step() * args.steps * world
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, wl.last_proof_bytes, rank, world)
 
     # roofline of the dominant kernel: its algorithmic bytes over its event-timed device time
     name, st = dominant, prof[dominant]
@@ -949,11 +984,12 @@ def main():
                               f"achieved = per-wave count x the live launches' waves / their live time"}
     # the HBM rate a plain device copy reaches on this box (1 GiB read + 1 GiB written), beside the
     # 8 TB/s spec the contract prices against ("measure actual HBM with a copy kernel")
-    copy = hbm_copy_gbs(ctx)
-    copy_gbs = copy["gbs"]
+    # (runs of their own after the timed steps: --full only)
+    copy = hbm_copy_gbs(ctx) if args.full else None
+    copy_gbs = copy["gbs"] if copy else None
     # the same kernel alone on the chip (in the prove, the boundary-quotient and randomizer
     # trees share the CUs with the main stream's algebra, which stretches their launches)
-    alone = standalone_launch(ctx, device, name, wl.fri_len)
+    alone = standalone_launch(ctx, device, name, wl.fri_len) if args.full else None
     phases = {k: {"launches": v["launches"], "ms_per_step": round(v["ms"], 4),
                   "GBps": round(v["bytes"] / (v["ms"] * 1e-3) / 1e9, 1) if v["ms"] > 0 else None}
               for k, v in sorted(breakdown.items(), key=lambda kv: -kv[1]["ms"])}
@@ -1021,14 +1057,14 @@ def main():
         "host_phases_ms": {k: round(v / args.steps * 1e3, 3) for k, v in host_phases.items()},
     }
     fri_len = wl.fri_len
-    if world == 1 and not args.no_side:
+    if args.full and world == 1 and not args.no_side:
         del wl
         ctx.trim()
         result["side"] = side_measurements(ctx, device)
         result["side"].update(block_and_c4(ctx, device))
         result["side"].update(rpsss_side(ctx))
         result["side"].update(c5_single_gpu(ctx, device))
-    if world > 1 and not args.no_side:
+    if args.full and world > 1 and not args.no_side:
         # a hang in a collective must not cost the main line: rank 0 prints it, and every rank
         # exits on its own timer (a rank left blocked in a collective would hold the launcher)
         # A hang exits NON-ZERO (a stuck collective on a process that has touched the GPU is a failure
@@ -1059,7 +1095,7 @@ def main():
             state["done"] = True
             watchdog.cancel()
             result["side"] = side
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         result["cpu_baseline"] = cpu_baseline_leg(fri_len)
         result["cpu_baseline_allcores"] = cpu_baseline_allcores(args.log_trace)
         result["cpu_baseline_e2e"] = cpu_baseline_e2e()

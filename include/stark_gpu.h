@@ -72,6 +72,9 @@ int sg_ctx_cached_tables(const sg_ctx* ctx, size_t* domain_tables, size_t* twidd
  *                    a gate left 60 s raises an error); 0: each round is launched after its challenge
  *   "fri_gate_timeout_ms" 60000 (default): how long a gate waits for its challenge before the call
  *                    fails with SG_ERR_HIP (a test sets it low to exercise the deadline)
+ *   "verify_device"  1 (default): the verifier's polynomial evaluations at the opened points, the
+ *                    transition zerofier there and the Merkle paths run on the device; 0: plain
+ *                    host loops over the same orchestration (same verdicts and messages)
  * SG_ERR_INVALID for an unknown name. */
 int sg_ctx_set_option(sg_ctx* ctx, const char* name, int64_t value);
 /* Device memory (no reference counterpart): `live` = bytes of the context's buffer pool in use,
@@ -137,6 +140,10 @@ int sg_merkle_commit(sg_ctx* ctx, const sg_fe* leaves, size_t n, uint8_t root[64
 int sg_merkle_open(sg_ctx* ctx, size_t index, const sg_fe* leaves, size_t n, uint8_t* path, size_t* path_len);
 /* merkle_root.rs:89-95  MerkleRoot::verify(root, index, path, leaf) -> bool: returns 1/0, < 0 on error */
 int sg_merkle_verify(const uint8_t root[64], size_t index, const uint8_t* path, size_t path_len, sg_fe leaf);
+/* merkle_root.rs:89-95 for n items; paths = n x stride x 64 bytes, depths[i] <= stride (NULL: all = stride);
+ * ok[i] = 1/0.  depth 0 or index >= 2^depth: SG_ERR_INVALID for the call (reference: unwrap / assert) */
+int sg_merkle_verify_batch(sg_ctx* ctx, const uint8_t* roots, const uint64_t* indices, const sg_fe* leaves,
+                           const uint8_t* paths, size_t stride, const uint32_t* depths, size_t n, uint8_t* ok);
 /* device-resident tree: build once, open in O(log n) */
 int sg_merkle_build_dev(sg_ctx* ctx, const sg_fe* d_leaves, size_t n, sg_tree** out);
 /* batch (1..4) equal-size trees built together (stark/stark.rs:380 commits one per register) */
@@ -179,6 +186,15 @@ int sg_stream_fiat_shamir_verifier(const sg_stream* s, size_t num_bytes, uint8_t
 int sg_stream_pull(sg_stream* s, uint8_t* code, const uint8_t** payload, size_t* len);
 /* stark/stark.rs:30-67 deser_independent_proof_stream */
 int sg_stream_deserialize(const uint8_t* bytes, size_t len, sg_stream** out);
+/* verifier's view of any ProofStream impl (proof_stream.rs:6-12): pull + fiat_shamir_verifier.
+ * pull returns 0, SG_ERR_INVALID when the stream is exhausted ("Cannot pull, queue is empty"), any
+ * other value for a failing callback (SG_ERR_CALLBACK to the caller) */
+typedef struct {
+  void* user;
+  int (*pull)(void* user, uint8_t* code, const uint8_t** payload, size_t* len); /* valid until the next pull */
+  int (*fiat_shamir_verifier)(void* user, size_t num_bytes, uint8_t* out);
+} sg_verifier_stream;
+sg_verifier_stream sg_stream_verifier_callbacks(sg_stream* s);
 
 /* ------------------------------------------------------------ FRI (fri.rs) */
 typedef struct {
@@ -208,6 +224,14 @@ void sg_fri_state_free(sg_ctx* ctx, sg_fri_state* st);
 /* fri.rs:88-113  FRI::sample_indices */
 int sg_fri_sample_indices(const uint8_t* seed, size_t seed_len, size_t size, size_t reduced_size,
                           size_t number, size_t* out);
+/* fri.rs:250-416  FRI::verify: 1 accepted, 0 rejected (sg_last_error = the reference's Err text), < 0 error
+ * (where the reference panics: SG_ERR_INVALID with its message; an element >= p: SG_ERR_NONCANONICAL).
+ * indices/values receive the 2c polynomial_values in the reference's push order; on a rejection or an
+ * error only the entries pushed before it are written.  The checks are decided in the reference's
+ * order (per round: the colinearity tests, then the aa, bb, cc paths): the Merkle paths of all rounds
+ * are checked in one batch and the first failure in that order is reported; a structural problem
+ * after the first rejecting check does not turn the rejection into an error. */
+int sg_fri_verify(sg_ctx* ctx, const sg_fri* fri, const sg_verifier_stream* vs, size_t* indices, sg_fe* values);
 
 
 /* ------------------------------------------------ row-sharded blocks (multi-GPU)
@@ -360,6 +384,14 @@ int sg_fast_interpolate_domain(sg_ctx* ctx, sg_fe root, uint64_t root_order, con
 int sg_fast_zerofier_geometric(sg_ctx* ctx, sg_fe root, uint64_t root_order, size_t n, sg_poly** out);
 int sg_fast_interpolate_geometric_dev(sg_ctx* ctx, sg_fe root, uint64_t root_order, const sg_fe* d_values,
                                       size_t n, sg_poly** out);
+/* field/polynomial.rs Polynomial::evaluate at nx points, npoly device polynomials: out[p*nx + j] */
+int sg_poly_evaluate_points(sg_ctx* ctx, const sg_poly* const* polys, size_t npoly, const sg_fe* xs, size_t nx,
+                            sg_fe* out);
+/* stark.rs:188-196 + :728  prod_{r<n}(x - root^r) for each x (n = 0: 1) */
+int sg_zerofier_geometric_at(sg_ctx* ctx, sg_fe root, uint64_t n, const sg_fe* xs, size_t nx, sg_fe* out);
+/* instrumentation, no reference counterpart: the two kernels' shape -- lanes per block (B) and
+ * coefficients / factors per block (C); lengths around them take the kernels' other paths */
+void sg_verify_kernel_shape(size_t* block, size_t* chunk);
 
 /* ------------------------------------------- multivariate polynomials (m_polynomial.rs)
  * MPolynomial {exponent vector: coefficient}; zero coefficients are kept as keys (the
@@ -430,6 +462,13 @@ int sg_stark_prove_dev(sg_ctx* ctx, const sg_stark* st, const sg_fe* d_trace, si
                        const sg_mpoly* const* tcs, size_t ntcs, const sg_boundary* boundary, size_t nb,
                        const sg_fe* d_trace_randomizers, const sg_fe* d_randomizer_coeffs, size_t n_rc,
                        const sg_proof_stream* ps);
+/* stark.rs:565-770 Stark::verify: 1 accepted, 0 rejected (sg_last_error = the reference's Err text,
+ * "FRI verification failed: ..." prefixed as the reference does), < 0 error as sg_fri_verify.  Order of
+ * the checks: FRI, the boundary-quotient openings tree by tree in sorted-index order, the randomizer
+ * openings, the combination per index.  The constraints are evaluated through their grouped form: the
+ * distinct x-polynomials at the 2c points on the device, combined with the register values on the host. */
+int sg_stark_verify(sg_ctx* ctx, const sg_stark* st, const sg_mpoly* const* tcs, size_t ntcs,
+                    const sg_boundary* boundary, size_t nb, const sg_verifier_stream* vs);
 /* stark.rs:276-562 Stark::prove with the codeword domain sharded over the communicator (replaces
  * Stark::prove when the FRI domain is split across GPUs).  Every rank passes the same arguments
  * (st and tcs created on the communicator's context, sg_dist_ctx) and writes the same proof-stream

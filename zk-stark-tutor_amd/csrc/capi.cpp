@@ -471,6 +471,7 @@ extern "C" int sg_ctx_set_option(sg_ctx* ctx, const char* name, int64_t value) {
   else if (n == "lean_drop" && value >= 0 && value <= 3) ctx->opt.lean_drop = (int)value;
   else if (n == "fri_gate") ctx->opt.fri_gate = v;
   else if (n == "fri_gate_timeout_ms" && value >= 1) ctx->opt.fri_gate_timeout_ms = value;
+  else if (n == "verify_device") ctx->opt.verify_device = v;
   else {
     ctx->last_error = "unknown context option: " + n;
     return SG_ERR_INVALID;

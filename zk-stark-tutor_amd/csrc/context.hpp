@@ -138,6 +138,7 @@ struct sg_ctx {
     int lean_drop = 3;           // the most levels a lean tree drops (0..3)
     bool fri_gate = true;        // FRI rounds queued behind a device gate before their challenge
     int64_t fri_gate_timeout_ms = 60000;  // a gate left this long times out (the call then fails)
+    bool verify_device = true;   // the verifier's three evaluations on the device (else plain host loops)
   } opt;
   bool domain_cache_on() const { return opt.domain_cache; }
   void* domain_table(const std::vector<uint64_t>& key) const;

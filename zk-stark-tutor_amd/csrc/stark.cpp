@@ -12,6 +12,7 @@
 //   openings of the boundary-quotient and randomizer codewords, serialized on the device
 //     together with the FRI query phase (TailWriter: one launch, one copy).
 // The thread_rng draws (trace randomizers, randomizer polynomial) are explicit inputs.
+// Stark::verify (stark.rs:565-770) is stark_verify below, over verify.hpp's stream walk and kernels.
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -34,6 +35,7 @@
 #include "mpoly.hpp"
 #include "poly.hpp"
 #include "poly_kernels.hpp"
+#include "verify.hpp"
 
 namespace sg {
 
@@ -1613,6 +1615,149 @@ void stark_prove_dist(sg_dist* dd, const sg_stark& st, const fe* d_trace, size_t
   check_div_zero(ctx);
 }
 
+// stark.rs:565-770 Stark::verify.  Returns 1, or 0 with the reference's Err text in msg; throws
+// where the reference panics.  The stream is walked in the reference's order; every Merkle opening
+// (FRI's and the 4c per tree of the tail) is queued and checked in one batch (verify.hpp), then the
+// combination is checked at the 2c points: the constraints' distinct x-polynomials and the
+// transition zerofier at all points on the device, the rest per point on the host.
+int stark_verify(sg_ctx* ctx, const sg_stark& st, const std::vector<const MPoly*>& tcs, const std::vector<Boundary>& bnd,
+                 const sg_verifier_stream* vs, std::string& msg) {
+  SG_REQUIRE(!bnd.empty(), "boundary is empty");
+  const size_t m = st.m;
+  const uint64_t Nf = st.fri.domain_length;
+  uint64_t otl = 0;
+  for (auto& b : bnd) otl = std::max(otl, b.cycle + 1);
+  const uint64_t rtl = otl + st.num_randomizers;
+
+  VStream in{vs};
+  PathQueue q;
+  std::vector<std::vector<uint8_t>> bq_roots;
+  std::vector<uint8_t> r_root;
+  std::vector<fe> weights;
+  std::vector<HPoly> bi;
+  std::vector<uint64_t> indices;
+  std::vector<fe> values;
+  std::vector<std::map<uint64_t, fe>> leafs(m);
+  std::map<uint64_t, fe> rnd;
+
+  const int walked = verify_in_order(ctx, q, msg, [&](std::string& why) {
+    for (size_t s = 0; s < m; ++s) bq_roots.push_back(in.root());
+    r_root = in.root();
+    bi = boundary_interpolants(st, bnd);
+    uint8_t fs[32];
+    in.fiat_shamir(32, fs);
+    weights = sample_weights(1 + 2 * tcs.size() + 2 * bi.size(), fs, 32);
+
+    std::vector<std::pair<uint64_t, fe>> points;
+    if (!fri_verify_walk(ctx, &st.fri, in, q, "FRI verification failed: ", points, why)) return 0;
+    std::stable_sort(points.begin(), points.end(),
+                     [](const std::pair<uint64_t, fe>& a, const std::pair<uint64_t, fe>& b) { return a.first < b.first; });
+    for (auto& p : points) {
+      indices.push_back(p.first);
+      values.push_back(p.second);
+    }
+    std::vector<uint64_t> dup = indices;
+    for (uint64_t i : indices) dup.push_back((i + st.expansion) % Nf);
+    std::sort(dup.begin(), dup.end());
+
+    // stark.rs:637-674: (Value, Path) per duplicated index, the boundary-quotient trees, then the randomizer's
+    for (size_t s = 0; s <= m; ++s) {
+      const std::vector<uint8_t>& root = s < m ? bq_roots[s] : r_root;
+      std::map<uint64_t, fe>& into = s < m ? leafs[s] : rnd;
+      for (uint64_t i : dup) {
+        const fe leaf = in.elements(SG_OBJ_VALUE, "value", 1)[0];
+        q.pull_path(in, root, i, leaf,
+                    s < m ? "Boundary quotient root " + std::to_string(i) + " is not verified"
+                          : "Randomizer leaf " + std::to_string(i) + " not verified");
+        into[i] = leaf;
+      }
+    }
+    return 1;
+  });
+  if (!walked) return 0;
+
+  // stark.rs:676-769: the combination at every point
+  const std::vector<HPoly> bz = boundary_zerofiers(st, bnd);
+  const uint64_t tcd = max_degree(st, tcs);
+  const std::vector<uint64_t> tqdb = transition_quotient_degree_bounds(st, tcs);
+  std::vector<uint64_t> bqdb;
+  for (size_t s = 0; s < m; ++s) {
+    const int64_t dz = hp_degree(bz[s]);
+    SG_REQUIRE(dz >= 0, "Couldnt get degree of boundary zerofier");
+    SG_REQUIRE(rtl - 1 >= (uint64_t)dz, "attempt to subtract with overflow");
+    bqdb.push_back(rtl - 1 - (uint64_t)dz);
+  }
+  for (size_t i = 0; i < tcs.size(); ++i) SG_REQUIRE(tcd >= tqdb[i], "attempt to subtract with overflow");
+  for (size_t s = 0; s < m; ++s) SG_REQUIRE(tcd >= bqdb[s], "attempt to subtract with overflow");
+  SG_REQUIRE(st.original_trace_length >= 1, "attempt to subtract with overflow");
+
+  const size_t np = indices.size();
+  std::vector<fe> xs(np), xn(np);
+  for (size_t j = 0; j < np; ++j) {
+    xs[j] = fe_mul(st.generator, fe_pow(st.omega, indices[j]));
+    xn[j] = fe_mul(st.generator, fe_pow(st.omega, (indices[j] + st.expansion) % Nf));
+  }
+  // the distinct x-polynomials of every constraint at the points, and the transition zerofier there
+  std::vector<std::shared_ptr<const MPolyDevice>> devs;
+  std::vector<EvalPolyRef> refs;
+  std::vector<size_t> first_ref;
+  for (const MPoly* tc : tcs) {
+    SG_REQUIRE(tc->g.empty() || tc->nvars <= 1 + 2 * m, "point has fewer values than the polynomial has variables");
+    devs.push_back(mp_device(ctx, *tc));
+    first_ref.push_back(refs.size());
+    for (size_t k = 0; k < devs.back()->ptr.size(); ++k)
+      refs.push_back({static_cast<const fe*>(devs.back()->ptr[k]), devs.back()->len[k]});
+  }
+  std::vector<fe> Q(refs.size() * np), zx(np);
+  eval_points(ctx, refs, xs.data(), np, Q.data());
+  zerofier_geometric_at(ctx, st.omicron, st.original_trace_length - 1, xs.data(), np, zx.data());
+
+  for (size_t j = 0; j < np; ++j) {
+    const uint64_t ic = indices[j], inx = (ic + st.expansion) % Nf;
+    std::vector<fe> point(1 + 2 * m);
+    point[0] = xs[j];
+    for (size_t s = 0; s < m; ++s) {
+      point[1 + s] = fe_add(fe_mul(leafs[s][ic], hp_eval(bz[s], xs[j])), hp_eval(bi[s], xs[j]));
+      point[1 + m + s] = fe_add(fe_mul(leafs[s][inx], hp_eval(bz[s], xn[j])), hp_eval(bi[s], xn[j]));
+    }
+    std::vector<fe> terms;
+    terms.push_back(rnd[ic]);
+    SG_REQUIRE(tcs.empty() || !fe_eq(zx[j], fe_zero()), "divide by zero");
+    const fe zinv = fe_inv(zx[j]);
+    for (size_t i = 0; i < tcs.size(); ++i) {
+      // m_polynomial.rs:95-122 through the groups: sum_g scale_g Q_g(x) prod_k v_k^e_gk
+      const MPolyDevice& d = *devs[i];
+      fe tv = fe_zero();
+      size_t g = 0;
+      for (auto& kv : tcs[i]->g) {
+        const int32_t qi = d.qidx[g];
+        if (qi >= 0) {
+          fe v = fe_mul(d.scale[g], Q[(first_ref[i] + (size_t)qi) * np + j]);
+          for (size_t k = 0; k < kv.first.size(); ++k)
+            if (kv.first[k]) v = fe_mul(v, fe_pow(point[k + 1], kv.first[k]));
+          tv = fe_add(tv, v);
+        }
+        ++g;
+      }
+      const fe quotient = fe_mul(tv, zinv);
+      terms.push_back(quotient);
+      terms.push_back(fe_mul(quotient, fe_pow(xs[j], tcd - tqdb[i])));
+    }
+    for (size_t s = 0; s < m; ++s) {
+      const fe bqv = leafs[s][ic];
+      terms.push_back(bqv);
+      terms.push_back(fe_mul(bqv, fe_pow(xs[j], tcd - bqdb[s])));
+    }
+    fe comb = fe_zero();
+    for (size_t k = 0; k < terms.size(); ++k) comb = fe_add(comb, fe_mul(terms[k], weights[k]));
+    if (!fe_eq(comb, values[j])) {
+      msg = "Combination doesn't match with polynomial value";
+      return 0;
+    }
+  }
+  return 1;
+}
+
 std::vector<const MPoly*> tc_list(const sg_mpoly* const* tcs, size_t n) {
   std::vector<const MPoly*> v;
   for (size_t i = 0; i < n; ++i) {
@@ -1808,6 +1953,26 @@ extern "C" int sg_stark_prove_dev(sg_ctx* ctx, const sg_stark* st, const sg_fe* 
                 reinterpret_cast<const fe*>(d_trace_randomizers), reinterpret_cast<const fe*>(d_randomizer_coeffs),
                 n_rc, ps);
   });
+}
+
+extern "C" int sg_stark_verify(sg_ctx* ctx, const sg_stark* st, const sg_mpoly* const* tcs, size_t ntcs,
+                               const sg_boundary* boundary, size_t nb, const sg_verifier_stream* vs) {
+  int verdict = 0;
+  const int rc = guard(ctx, [&] {
+    SG_REQUIRE(ctx && st && (tcs || !ntcs) && (boundary || !nb), "null argument");
+    SG_REQUIRE(vs && vs->pull && vs->fiat_shamir_verifier, "verifier stream callbacks required");
+    set_device(ctx);
+    std::vector<Boundary> bnd;
+    for (size_t i = 0; i < nb; ++i) {
+      check_canonical(&boundary[i].value, 1, "boundary value");
+      SG_REQUIRE(boundary[i].reg < st->m, "boundary register out of range");
+      bnd.push_back({boundary[i].cycle, boundary[i].reg, to_fe(boundary[i].value)});
+    }
+    std::string msg;
+    verdict = stark_verify(ctx, *st, tc_list(tcs, ntcs), bnd, vs, msg);
+    ctx->last_error = verdict ? "" : msg;
+  });
+  return rc < 0 ? rc : verdict;
 }
 
 // ====================================================================== C ABI: sharded STARK

@@ -46,6 +46,20 @@ class sg_proof_stream(ctypes.Structure):
     _fields_ = [("user", ctypes.c_void_p), ("push", PUSH_CB), ("fiat_shamir_prover", FS_CB)]
 
 
+PULL_CB = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint8),
+                           ctypes.POINTER(ctypes.POINTER(ctypes.c_uint8)), ctypes.POINTER(ctypes.c_size_t))
+
+
+class sg_verifier_stream(ctypes.Structure):
+    _fields_ = [("user", ctypes.c_void_p), ("pull", PULL_CB), ("fiat_shamir_verifier", FS_CB)]
+
+
+# shape of the verifier's evaluation kernels (sg_verify_kernel_shape; a CPU test keeps them equal
+# to the library's): lanes per block, and coefficients / factors per block
+EVAL_BLOCK = 256
+EVAL_CHUNK = 8192
+
+
 A2A_CB = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t)
 
 
@@ -196,6 +210,14 @@ PROTOTYPES = {
                                       _P(sg_proof_stream)]),
     "sg_stark_prove_dev": (ctypes.c_int, [_vp, _vp, _vp, _sz, _vp, _sz, _vp, _sz, _vp, _vp, _sz,
                                           _P(sg_proof_stream)]),
+    # verifier (fri.rs:250-416, stark.rs:565-770)
+    "sg_merkle_verify_batch": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _sz, _vp, _sz, _vp]),
+    "sg_stream_verifier_callbacks": (sg_verifier_stream, [_vp]),
+    "sg_fri_verify": (ctypes.c_int, [_vp, _P(sg_fri), _P(sg_verifier_stream), _P(_sz), _vp]),
+    "sg_poly_evaluate_points": (ctypes.c_int, [_vp, _P(_vp), _sz, _vp, _sz, _vp]),
+    "sg_zerofier_geometric_at": (ctypes.c_int, [_vp, sg_fe, ctypes.c_uint64, _vp, _sz, _vp]),
+    "sg_verify_kernel_shape": (None, [_P(_sz), _P(_sz)]),
+    "sg_stark_verify": (ctypes.c_int, [_vp, _vp, _vp, _sz, _vp, _sz, _P(sg_verifier_stream)]),
     "sg_dist_stark_prove": (ctypes.c_int, [_vp, _vp, _vp, _sz, _vp, _sz, _vp, _sz, _vp, _vp, _sz,
                                            _P(sg_proof_stream)]),
     "sg_dist_stark_prove_dev": (ctypes.c_int, [_vp, _vp, _vp, _sz, _vp, _sz, _vp, _sz, _vp, _vp, _sz,

@@ -126,6 +126,29 @@ def fast_zerofier_geometric(root: int, root_order: int, n: int, ctx: Optional[Co
     return _poly_out(c, c._lib.sg_fast_zerofier_geometric(c.handle, _fe(root), root_order, n, ctypes.byref(h)), h)
 
 
+def evaluate_points(polys: Sequence, xs: Sequence[int], ctx: Optional[Context] = None) -> List[List[int]]:
+    """field/polynomial.rs Polynomial::evaluate of every polynomial (a `Polynomial` or a coefficient
+    list) at every point, in one batch on the device: out[p][j] = polys[p](xs[j])."""
+    c = _ctx(ctx)
+    ps = [_as_poly(p, c) for p in polys]
+    x = fe_array(xs)
+    out = np.zeros((max(len(ps) * len(x), 1), 2), dtype=np.uint64)
+    handles = (ctypes.c_void_p * max(len(ps), 1))(*[p.handle.value for p in ps])
+    c.check(c._lib.sg_poly_evaluate_points(c.handle, handles, len(ps), _ptr(x), len(x), _ptr(out)))
+    flat = to_ints(out)
+    return [flat[p * len(x):(p + 1) * len(x)] for p in range(len(ps))]
+
+
+def zerofier_geometric_at(root: int, n: int, xs: Sequence[int], ctx: Optional[Context] = None) -> List[int]:
+    """prod_{r < n} (x - root^r) for each x: what Stark::transition_zerofier().evaluate(x) equals
+    (stark.rs:188-196, :728), without the zerofier's coefficients."""
+    c = _ctx(ctx)
+    x = fe_array(xs)
+    out = np.zeros((max(len(x), 1), 2), dtype=np.uint64)
+    c.check(c._lib.sg_zerofier_geometric_at(c.handle, _fe(root), n, _ptr(x), len(x), _ptr(out)))
+    return to_ints(out)[:len(x)]
+
+
 def fast_interpolate_geometric_dev(root: int, root_order: int, d_values: int, n: int,
                                    ctx: Optional[Context] = None) -> Polynomial:
     """fast_interpolate_domain on root^0 .. root^(n-1) with device-resident values."""

@@ -20,7 +20,8 @@ from typing import Iterable, List, Optional, Sequence, Tuple, Union
 
 import numpy as np
 
-from ._lib import (PUSH_CB, FS_CB, StarkGpuError, lib, sg_fe, sg_fri, sg_proof_stream)
+from ._lib import (EVAL_BLOCK, EVAL_CHUNK, PUSH_CB, FS_CB, PULL_CB, StarkGpuError, lib, sg_fe, sg_fri,
+                   sg_proof_stream, sg_verifier_stream)
 
 FIELD_PRIME = 1 + 407 * (1 << 119)
 MASK64 = (1 << 64) - 1
@@ -135,7 +136,8 @@ class Context:
 
     def set_option(self, name: str, value) -> None:
         """sg_ctx_set_option: "domain_cache", "air_generic", "geo_decimate", "lean_trees", "stream_pin",
-        "world1_sharded", "lean_drop" -- equivalent paths (same proof bytes) that the tests compare."""
+        "world1_sharded", "lean_drop", "fri_gate", "verify_device" -- equivalent paths (same proof
+        bytes, same verdicts) that the tests compare."""
         self.check(self._lib.sg_ctx_set_option(self.handle, name.encode(), int(value)))
 
     @contextlib.contextmanager
@@ -335,6 +337,33 @@ class MerkleRoot:
             raise StarkGpuError(rc, "Cannot verify invalid index")
         return rc == 1
 
+    @staticmethod
+    def verify_batch(roots: Sequence[bytes], indices: Sequence[int], leaves, paths: Sequence[Sequence[bytes]],
+                     ctx: Optional[Context] = None) -> List[bool]:
+        """merkle_root.rs:89-95 for many (root, index, leaf, path) items in one device launch; the
+        paths may differ in depth.  An empty path or index >= 2^depth raises (the reference panics)."""
+        c = _ctx(ctx)
+        n = len(roots)
+        if not (len(indices) == n and len(paths) == n and len(leaves) == n):
+            raise ValueError("roots, indices, leaves and paths must have one entry per item")
+        if n == 0:
+            return []
+        if any(len(r) != 64 for r in roots) or any(len(b) != 64 for p in paths for b in p):
+            raise ValueError("roots and path nodes are 64-byte digests")
+        stride = max(1, max(len(p) for p in paths))
+        depths = np.array([len(p) for p in paths], dtype=np.uint32)
+        praw = np.zeros((n, stride * 64), dtype=np.uint8)
+        for i, p in enumerate(paths):
+            if p:
+                praw[i, :64 * len(p)] = np.frombuffer(b"".join(p), dtype=np.uint8)
+        rraw = np.frombuffer(b"".join(roots), dtype=np.uint8).copy()
+        idx = np.array([int(i) for i in indices], dtype=np.uint64)
+        lv = fe_array(leaves)
+        ok = np.zeros(n, dtype=np.uint8)
+        c.check(c._lib.sg_merkle_verify_batch(c.handle, _ptr(rraw), _ptr(idx), _ptr(lv), _ptr(praw), stride,
+                                              _ptr(depths), n, _ptr(ok)))
+        return [bool(v) for v in ok]
+
 
 class DeviceTree:
     """A retained device Merkle tree (build once, open in O(log n))."""
@@ -506,6 +535,9 @@ class IndependentProofStream:
     def callbacks(self) -> sg_proof_stream:
         return self._lib.sg_stream_callbacks(self.handle)
 
+    def verifier_callbacks(self) -> sg_verifier_stream:
+        return self._lib.sg_stream_verifier_callbacks(self.handle)
+
     def __del__(self):
         try:
             if self.handle:
@@ -547,17 +579,65 @@ class CallbackProofStream:
                 self.error = e
                 return 1
 
+        def _pull(user, code, payload, n):
+            try:
+                c, data = encode_object(self.inner.pull())
+                # the view stays valid until the next pull: the adapter holds the buffer
+                self._held = (ctypes.c_uint8 * max(len(data), 1)).from_buffer_copy(data if data else b"\0")
+                code[0] = c
+                payload[0] = ctypes.cast(self._held, ctypes.POINTER(ctypes.c_uint8))
+                n[0] = len(data)
+                return 0
+            except Exception as e:  # an exhausted stream included: the reference's unwrap panics
+                self.error = e
+                return 1
+
+        def _fsv(user, n, out):
+            try:
+                b = self.inner.fiat_shamir_verifier(n)
+                ctypes.memmove(out, b, n)
+                return 0
+            except Exception as e:
+                self.error = e
+                return 1
+
         self._push = PUSH_CB(_push)
         self._fs = FS_CB(_fs)
+        self._pull = PULL_CB(_pull)
+        self._fsv = FS_CB(_fsv)
+        self._held = None
 
     def callbacks(self) -> sg_proof_stream:
         return sg_proof_stream(None, self._push, self._fs)
+
+    def verifier_callbacks(self) -> sg_verifier_stream:
+        """pull + fiat_shamir_verifier of the wrapped stream (proof_stream.rs:6-12)."""
+        return sg_verifier_stream(None, self._pull, self._fsv)
+
+
+def _verifier_stream(proof_stream):
+    """(sg_verifier_stream, adapter or None) of a native stream or of any Python ProofStream."""
+    if isinstance(proof_stream, IndependentProofStream):
+        return proof_stream.verifier_callbacks(), None
+    adapter = CallbackProofStream(proof_stream)
+    return adapter.verifier_callbacks(), adapter
+
+
+def _verdict(ctx: "Context", rc: int, adapter) -> Tuple[bool, str]:
+    """1 / 0 / < 0 of sg_fri_verify and sg_stark_verify -> (ok, err); errors raise."""
+    if rc < 0:
+        if adapter is not None and adapter.error is not None:
+            raise adapter.error
+        ctx.check(rc)
+    if rc == 1:
+        return True, ""
+    return False, ctx._lib.sg_last_error(ctx.handle).decode(errors="replace")
 
 
 # ------------------------------------------------------------------ FRI
 
 class FRI:
-    """fri.rs:13-248 on the GPU (commit, prove); the verifier side stays on the host."""
+    """fri.rs:13-416 on the GPU (commit, prove, verify)."""
 
     def __init__(self, offset: int, omega: int, domain_length: int, expansion_factor: int,
                  num_colinearity_tests: int, ctx: Optional[Context] = None):
@@ -607,6 +687,20 @@ class FRI:
             raise adapter.error
         self.ctx.check(rc)
         return list(out)[:self.num_colinearity_tests]
+
+    def verify(self, proof_stream) -> Tuple[bool, str, List[Tuple[int, int]]]:
+        """fri.rs:250-416: (ok, error, polynomial_values); the Merkle paths are checked on the GPU.
+        Raises where the reference panics (wrong object kind, exhausted stream, invalid index)."""
+        c = self.num_colinearity_tests
+        none = (1 << 64) - 1
+        idx = (ctypes.c_size_t * max(2 * c, 1))(*([none] * max(2 * c, 1)))
+        vals = np.zeros((max(2 * c, 1), 2), dtype=np.uint64)
+        vs, adapter = _verifier_stream(proof_stream)
+        rc = self.ctx._lib.sg_fri_verify(self.ctx.handle, ctypes.byref(self._p), ctypes.byref(vs), idx, _ptr(vals))
+        ok, err = _verdict(self.ctx, rc, adapter)
+        filled = [i for i in range(2 * c) if idx[i] != none]
+        v = to_ints(vals)
+        return ok, err, [(int(idx[i]), v[i]) for i in filled]
 
     def commit_dev(self, d_codeword: int, n: int, proof_stream) -> None:
         cb, adapter = self._stream(proof_stream)

@@ -15,7 +15,8 @@ from typing import Dict, List, Optional, Sequence, Tuple
 import numpy as np
 
 from ._lib import StarkGpuError, sg_fe, sg_fri
-from .api import (CallbackProofStream, Context, IndependentProofStream, _ctx, _fe, _int, _ptr, fe_array, to_ints)
+from .api import (CallbackProofStream, Context, IndependentProofStream, _ctx, _fe, _int, _ptr, _verdict,
+                  _verifier_stream, fe_array, to_ints)
 
 
 class sg_boundary(ctypes.Structure):
@@ -181,7 +182,7 @@ class RescuePrime:
 
 
 class Stark:
-    """stark/stark.rs Stark (the prover on the GPU)."""
+    """stark/stark.rs Stark (the prover and the verifier on the GPU)."""
 
     def __init__(self, expansion_factor: int, num_colinearity_checks: int, security_level: int, num_registers: int,
                  num_cycles: int, transition_constraints_degree: int = 2, ctx: Optional[Context] = None):
@@ -287,6 +288,17 @@ class Stark:
             dist._torch_ready()
             rcode = self.ctx._lib.sg_dist_stark_prove_dev(dist.handle, *args)
         self._finish(rcode, adapter)
+
+    def verify(self, transition_constraints: Sequence[MPolynomial], boundary: Sequence[Tuple[int, int, int]],
+               proof_stream) -> Tuple[bool, str]:
+        """stark.rs:565-770: (ok, error text of the reference's Err).  The Merkle paths, the
+        constraints' x-polynomials at the opened points and the transition zerofier there run on
+        the GPU.  Raises where the reference panics (wrong object kind, exhausted stream, ...)."""
+        bnd = (sg_boundary * max(len(boundary), 1))(*[sg_boundary(c, r, _fe(v)) for (c, r, v) in boundary])
+        vs, adapter = _verifier_stream(proof_stream)
+        rc = self.ctx._lib.sg_stark_verify(self.ctx.handle, self.handle, self._tcs(transition_constraints),
+                                           len(transition_constraints), bnd, len(boundary), ctypes.byref(vs))
+        return _verdict(self.ctx, rc, adapter)
 
     def __del__(self):
         try:

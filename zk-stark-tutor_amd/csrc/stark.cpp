@@ -450,10 +450,6 @@ AirCoset air_coset(sg_ctx* ctx, const std::vector<DPoly>& trace_polys, uint64_t 
   return c;
 }
 
-
-// A Rescue-Prime row in its factored form (mpoly.hpp RescueAirForm) on the coset: the same values
-// as the expanded polynomial.  Its round-constant interpolants' coset values are public and kept
-// with the AIR (like the x-polynomial values of the generic path).
 // values of a Rescue AIR x-polynomial (first_i / second_k) on offset * <w_L>, kept in the
 // context's domain tables (content-keyed) unless SG_NO_DOMAIN_CACHE=1 (then owned by `keep`)
 const fe* rescue_xvals(sg_ctx* ctx, const RescueAirForm& f, int idx, uint64_t L, const fe& offset,
@@ -947,8 +943,9 @@ void prove_boundary_quotients(sg_ctx* ctx, const sg_stark& st, const std::vector
   }
 }
 
-// transition quotients (stark.rs:388-422) and every quotient's degree (one host round trip; a zero
-// divisor is reported here, before any root is pushed)
+// transition quotients (stark.rs:388-422) and every quotient's degree (one host round trip, which
+// also reports a zero divisor: by then `overlap` has pushed the boundary and randomizer roots and
+// drawn the weights)
 //
 // With `dd` (the sharded prove) and a native Rescue-Prime AIR, the coset work is
 // split over the communicator: each rank evaluates the trace polynomials on its run shard of the
@@ -1161,7 +1158,8 @@ void prove_transition_quotients(sg_ctx* ctx, const sg_stark& st, const std::vect
   }
   // every quotient's degree with one host round trip (checked after the weights, as the
   // reference does, and used again by the terms below); it drains the main stream past
-  // every division, so a zero divisor is reported before any root is pushed
+  // every division, so a zero divisor is reported right after it -- `overlap` has by then pushed
+  // the boundary and randomizer roots and drawn the weights
   auto quotient_degrees = [&]() {
     std::vector<std::pair<const fe*, uint64_t>> qpolys;
     for (const DPoly& q : tqs) qpolys.emplace_back(q.p(), q.len);

@@ -75,6 +75,11 @@ int sg_ctx_cached_tables(const sg_ctx* ctx, size_t* domain_tables, size_t* twidd
  *   "verify_device"  1 (default): the verifier's polynomial evaluations at the opened points, the
  *                    transition zerofier there and the Merkle paths run on the device; 0: plain
  *                    host loops over the same orchestration (same verdicts and messages)
+ *   "rescue_device_min" 32 (default, the measured crossover at m = 2, N = 27: the host loop takes 50 us
+ *                    per hash, the device call 1.2-1.4 ms for any batch up to one wave per SIMD):
+ *                    sg_rescue_hash_batch / _trace_batch (and sg_rpsss_keygen_batch through them) run
+ *                    the host loop below this many inputs, the device kernel from it on (same
+ *                    values); 0: always the device
  * SG_ERR_INVALID for an unknown name. */
 int sg_ctx_set_option(sg_ctx* ctx, const char* name, int64_t value);
 /* Device memory (no reference counterpart): `live` = bytes of the context's buffer pool in use,
@@ -436,6 +441,22 @@ int sg_rescue_trace(sg_ctx* ctx, const sg_rescue* rp, sg_fe input, sg_fe* trace)
 int sg_rescue_transition_constraints(sg_ctx* ctx, const sg_rescue* rp, sg_fe omicron,
                                      uint64_t omicron_domain_length, sg_mpoly** out);
 int sg_rescue_boundary_constraints(const sg_rescue* rp, sg_fe output, sg_boundary* out); /* :285-290, 2 */
+/* Batch forms: n independent inputs (capacity 1), e.g. RPSSS key generation or the traces of many
+ * signers.  One hash is a serial chain and stays on the host; a batch runs one lane per input on the
+ * device.  n = 0 is SG_OK and writes nothing.
+ * Host-pointer forms: every input is checked first (SG_ERR_NONCANONICAL names the first index >= p and
+ * nothing is written).  They run a host loop on a NULL context, for a state size without a kernel
+ * (kernels exist for m = 2, 3, 4) and for n below the context option "rescue_device_min"; otherwise
+ * upload, launch, download.  Both paths return the same values.
+ * _dev forms: device pointers, m in {2, 3, 4} (else SG_ERR_INVALID), inputs >= p undefined as for the
+ * other _dev entry points; they honour sg_ctx_set_async. */
+/* rescue_prime.rs:185-192 RescuePrime::hash for n inputs: out[i] = hash(inputs[i]) */
+int sg_rescue_hash_batch(sg_ctx* ctx, const sg_rescue* rp, const sg_fe* inputs, size_t n, sg_fe* out);
+int sg_rescue_hash_batch_dev(sg_ctx* ctx, const sg_rescue* rp, const sg_fe* d_inputs, size_t n, sg_fe* d_out);
+/* rescue_prime.rs:194-204 RescuePrime::trace for n inputs: n x (N+1) x m, input i's trace is the
+ * contiguous (N+1) x m block sg_rescue_trace writes (a valid d_trace of sg_stark_prove_dev) */
+int sg_rescue_trace_batch(sg_ctx* ctx, const sg_rescue* rp, const sg_fe* inputs, size_t n, sg_fe* traces);
+int sg_rescue_trace_batch_dev(sg_ctx* ctx, const sg_rescue* rp, const sg_fe* d_inputs, size_t n, sg_fe* d_traces);
 
 /* ------------------------------------------- STARK (stark/stark.rs) */
 typedef struct sg_stark sg_stark;
@@ -482,6 +503,36 @@ int sg_dist_stark_prove_dev(sg_dist* d, const sg_stark* st, const sg_fe* d_trace
                             const sg_mpoly* const* tcs, size_t ntcs, const sg_boundary* boundary, size_t nb,
                             const sg_fe* d_trace_randomizers, const sg_fe* d_randomizer_coeffs, size_t n_rc,
                             const sg_proof_stream* ps);
+
+/* ------------------------------------------- RPSSS (rpsss.rs): the Rescue-Prime STARK signature scheme
+ * The object owns its RescuePrime, its Stark and the m transition constraints, built once at creation
+ * (the reference rebuilds them for every sign and verify, rpsss.rs:46,57); no later call rebuilds them
+ * or adds to the context's table cache.  Creation, sign and verify need a GPU context. */
+typedef struct sg_rpsss sg_rpsss;
+/* rpsss.rs:16-36 RPSSS::new: RescuePrime::new(field, 2, 1, security_level, 27) under
+ * Stark::new(field, expansion_factor, num_colinearity_checks, security_level, rp.m, rp.N + 1,
+ * transition_constraints_degree) */
+int sg_rpsss_create(sg_ctx* ctx, size_t expansion_factor, size_t num_colinearity_checks, size_t security_level,
+                    size_t transition_constraints_degree, sg_rpsss** out);
+void sg_rpsss_free(sg_rpsss* r);
+/* the thread_rng values one sign takes (stark.rs:285-301, 425-433): num_randomizers x m trace
+ * randomizers, then the randomizer polynomial's coefficients */
+int sg_rpsss_params(const sg_rpsss* r, size_t* n_trace_randomizers, size_t* n_randomizer_coeffs);
+/* rpsss.rs:61-68 RPSSS::keygen: sk = Field::sample(seed), pk = hash(sk); thread_rng's 17 bytes are an
+ * explicit input (as the draws of Stark::prove are) */
+int sg_rpsss_keygen(sg_ctx* ctx, const sg_rpsss* r, const uint8_t seed[17], sg_fe* sk, sg_fe* pk);
+/* the same for n seeds (n x 17 bytes): sampled on the host, hashed through sg_rescue_hash_batch */
+int sg_rpsss_keygen_batch(sg_ctx* ctx, const sg_rpsss* r, const uint8_t* seeds, size_t n, sg_fe* sk, sg_fe* pk);
+/* rpsss.rs:70-73 RPSSS::sign (through :38-49 stark_prove): *out is a new SignatureProofStream of the
+ * document whose sg_stream_digest is the signature; the caller destroys it.  Argument errors and Err
+ * texts are those of sg_stark_prove. */
+int sg_rpsss_sign(sg_ctx* ctx, const sg_rpsss* r, sg_fe sk, const uint8_t* document, size_t doc_len,
+                  const sg_fe* trace_randomizers, const sg_fe* randomizer_coeffs, size_t n_rc, sg_stream** out);
+/* rpsss.rs:75-79 RPSSS::verify (through :51-59 stark_verify): 1 accepted, 0 rejected (sg_last_error = the
+ * reference's Err text), < 0 error; a signature that does not deserialize (stark.rs:30-67) is
+ * SG_ERR_INVALID */
+int sg_rpsss_verify(sg_ctx* ctx, const sg_rpsss* r, sg_fe pk, const uint8_t* document, size_t doc_len,
+                    const uint8_t* signature, size_t sig_len);
 
 #ifdef __cplusplus
 }

@@ -472,6 +472,7 @@ extern "C" int sg_ctx_set_option(sg_ctx* ctx, const char* name, int64_t value) {
   else if (n == "fri_gate") ctx->opt.fri_gate = v;
   else if (n == "fri_gate_timeout_ms" && value >= 1) ctx->opt.fri_gate_timeout_ms = value;
   else if (n == "verify_device") ctx->opt.verify_device = v;
+  else if (n == "rescue_device_min" && value >= 0) ctx->opt.rescue_device_min = value;
   else {
     ctx->last_error = "unknown context option: " + n;
     return SG_ERR_INVALID;
@@ -942,10 +943,6 @@ extern "C" int sg_merkle_verify(const uint8_t root[64], size_t index, const uint
 }
 
 // ======================================================================== C ABI: proof streams
-
-struct sg_stream {
-  Stream s;
-};
 
 namespace {
 int stream_push_cb(void* user, uint8_t code, const uint8_t* payload, size_t len) {

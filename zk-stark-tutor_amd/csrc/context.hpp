@@ -139,6 +139,9 @@ struct sg_ctx {
     bool fri_gate = true;        // FRI rounds queued behind a device gate before their challenge
     int64_t fri_gate_timeout_ms = 60000;  // a gate left this long times out (the call then fails)
     bool verify_device = true;   // the verifier's three evaluations on the device (else plain host loops)
+    // host-pointer Rescue-Prime batches (sg_rescue_hash_batch / _trace_batch) below this many inputs
+    // run the host loop: the measured crossover; 0 = always the device
+    int64_t rescue_device_min = 32;
   } opt;
   bool domain_cache_on() const { return opt.domain_cache; }
   void* domain_table(const std::vector<uint64_t>& key) const;

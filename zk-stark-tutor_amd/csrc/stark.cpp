@@ -24,6 +24,7 @@
 #include <map>
 #include <cstring>
 #include <memory>
+#include <mutex>
 #include <numeric>
 #include <string>
 #include <vector>
@@ -35,6 +36,8 @@
 #include "mpoly.hpp"
 #include "poly.hpp"
 #include "poly_kernels.hpp"
+#include "rescue_kernels.hpp"
+#include "rescue_pow.hpp"
 #include "verify.hpp"
 
 namespace sg {
@@ -144,11 +147,25 @@ using namespace sg;
 
 // ====================================================================== Rescue-Prime
 
+// the batch kernel's constants on one device (rescue_kernels.hpp: MDS, then the round constants,
+// Montgomery form)
+struct RescueDevice {
+  void* consts = nullptr;
+  ~RescueDevice() {
+    if (consts) (void)hipFree(consts);
+  }
+};
+
 struct sg_rescue {
   size_t m = 0, capacity = 0, security = 0, N = 0;
   unsigned __int128 alpha = 0, alpha_inv = 0;  // exponents (rescue_prime.rs:120-123)
   Mat mds, mds_inv;
   std::vector<fe> rc;  // 2 m N round constants
+  // batch paths: the m x m MDS matrix row-major, then rc, in Montgomery form (converted once), and
+  // their copies on the devices that ran a batch, made on first use and kept like a constraint's
+  // (mpoly.hpp MPoly::dev)
+  std::vector<fe> consts_m;
+  mutable std::map<int, std::shared_ptr<const RescueDevice>> dev;
 
   // rescue_prime.rs:52-106, one round r
   void round(std::vector<fe>& state, size_t r) const {
@@ -205,6 +222,9 @@ void rescue_init(sg_rescue& rp, size_t m, size_t capacity, size_t security, size
     for (int j = 15; j >= 0; --j) L = (L << 8) | c[j];
     rp.rc[i] = fe_add(fe_from_u128(L % p), fe_mul(fe_from_u64(c[16]), two128));
   }
+  for (size_t j = 0; j < m; ++j)
+    for (size_t i = 0; i < m; ++i) rp.consts_m.push_back(to_mont(rp.mds[j][i]));
+  for (const fe& c : rp.rc) rp.consts_m.push_back(to_mont(c));
 }
 
 std::vector<fe> rescue_trace(const sg_rescue& rp, const fe& input) {
@@ -218,6 +238,147 @@ std::vector<fe> rescue_trace(const sg_rescue& rp, const fe& input) {
     out.insert(out.end(), state.begin(), state.end());
   }
   return out;
+}
+
+// ---- batch forms (rescue_prime.rs:185-204 for n inputs): the host loop and the device launch run
+// the same rounds (rescue_pow.hpp) on a Montgomery state and return the values of sg_rescue::round
+
+// the batch paths hard-code the two exponents the field fixes
+void rescue_check_exponents(const sg_rescue& rp) {
+  SG_REQUIRE(rp.alpha == kRescueAlpha &&
+                 rp.alpha_inv == (((unsigned __int128)kRescueAlphaInvHi << 64) | kRescueAlphaInvLo),
+             "Rescue-Prime batch: alpha / alpha_inv are not the constants of this field");
+}
+
+template <int M>
+void rescue_host_one(const sg_rescue& rp, const fe& x, fe* out, bool trace) {
+  const fe* mds = rp.consts_m.data();
+  const fe* rc = mds + M * M;
+  fe s[M];
+  s[0] = to_mont(x);
+  for (int k = 1; k < M; ++k) s[k] = fe_zero();
+  if (trace)
+    for (int k = 0; k < M; ++k) out[k] = k ? fe_zero() : x;
+  for (size_t r = 0; r < rp.N; ++r) {
+    rescue_round<M>(s, mds, rc + 2 * M * r);
+    if (trace)
+      for (int k = 0; k < M; ++k) out[(r + 1) * M + k] = from_mont(s[k]);
+  }
+  if (!trace) *out = from_mont(s[0]);
+}
+
+// any m: the same round over vectors, one element's chain at a time
+void rescue_host_one_any(const sg_rescue& rp, const fe& x, fe* out, bool trace) {
+  const size_t m = rp.m;
+  const fe* mds = rp.consts_m.data();
+  const fe* rc = mds + m * m;
+  std::vector<fe> s(m, fe_zero()), t(m);
+  s[0] = to_mont(x);
+  if (trace)
+    for (size_t k = 0; k < m; ++k) out[k] = k ? fe_zero() : x;
+  auto mix = [&](const std::vector<fe>& in, std::vector<fe>& o, const fe* c) {
+    for (size_t j = 0; j < m; ++j) {
+      fe acc = c[j];
+      for (size_t i = 0; i < m; ++i) acc = fe_add(acc, mont_mul(in[i], mds[j * m + i]));
+      o[j] = acc;
+    }
+  };
+  for (size_t r = 0; r < rp.N; ++r) {
+    for (size_t k = 0; k < m; ++k) {
+      fe one[1] = {s[k]};
+      rescue_pow_alpha<1>(one);
+      s[k] = one[0];
+    }
+    mix(s, t, rc + 2 * m * r);
+    for (size_t k = 0; k < m; ++k) {
+      fe one[1] = {t[k]};
+      rescue_pow_alpha_inv<1>(one);
+      t[k] = one[0];
+    }
+    mix(t, s, rc + 2 * m * r + m);
+    if (trace)
+      for (size_t k = 0; k < m; ++k) out[(r + 1) * m + k] = from_mont(s[k]);
+  }
+  if (!trace) *out = from_mont(s[0]);
+}
+
+void rescue_batch_host(const sg_rescue& rp, const fe* in, size_t n, fe* out, bool trace) {
+  rescue_check_exponents(rp);
+  const size_t per = trace ? (rp.N + 1) * rp.m : 1;
+  for (size_t i = 0; i < n; ++i) {
+    fe* o = out + i * per;
+    switch (rp.m) {
+      case 2: rescue_host_one<2>(rp, in[i], o, trace); break;
+      case 3: rescue_host_one<3>(rp, in[i], o, trace); break;
+      case 4: rescue_host_one<4>(rp, in[i], o, trace); break;
+      default: rescue_host_one_any(rp, in[i], o, trace); break;
+    }
+  }
+}
+
+bool rescue_has_kernel(const sg_rescue& rp) {
+  return rp.m >= (size_t)kRescueBatchMinM && rp.m <= (size_t)kRescueBatchMaxM;
+}
+
+std::shared_ptr<const RescueDevice> rescue_device(sg_ctx* ctx, const sg_rescue& rp) {
+  static std::mutex mu;  // contexts on several host threads may share one sg_rescue
+  std::lock_guard<std::mutex> lk(mu);
+  auto hit = rp.dev.find(ctx->device);
+  if (hit != rp.dev.end()) return hit->second;
+  auto d = std::make_shared<RescueDevice>();
+  const size_t bytes = rp.consts_m.size() * sizeof(fe);
+  SG_HIP(hipMalloc(&d->consts, bytes));
+  SG_HIP(hipMemcpy(d->consts, rp.consts_m.data(), bytes, hipMemcpyHostToDevice));
+  rp.dev[ctx->device] = d;
+  return d;
+}
+
+// enqueues the batch on the context's stream (device pointers)
+void rescue_batch_launch(sg_ctx* ctx, const sg_rescue& rp, const fe* d_in, size_t n, fe* d_out, bool trace) {
+  rescue_check_exponents(rp);
+  SG_REQUIRE(rp.N <= 0xFFFFFFFFu, "Rescue-Prime batch: too many rounds");
+  auto d = rescue_device(ctx, rp);
+  SG_HIP(launch_rescue_batch((int)rp.m, trace, d_in, n, (uint32_t)rp.N, static_cast<const fe*>(d->consts), d_out,
+                             fe_r2(), ctx->stream));
+}
+
+int rescue_batch_entry(sg_ctx* ctx, const sg_rescue* rp, const sg_fe* inputs, size_t n, sg_fe* out, bool trace) {
+  return guard(ctx, [&] {
+    SG_REQUIRE(rp && (!n || (inputs && out)), "null argument");
+    SG_REQUIRE(rp->capacity == 1, "Received wrong number of input elements");
+    if (!n) return;
+    for (size_t i = 0; i < n; ++i)
+      if (!fe_is_canonical(to_fe(inputs[i])))
+        throw Error{SG_ERR_NONCANONICAL, "input " + std::to_string(i) + ": element >= p"};
+    const fe* in = reinterpret_cast<const fe*>(inputs);
+    fe* o = reinterpret_cast<fe*>(out);
+    // option rescue_device_min: batches below it stay on the host (same values either way)
+    if (!ctx || !rescue_has_kernel(*rp) || (uint64_t)n < (uint64_t)ctx->opt.rescue_device_min) {
+      rescue_batch_host(*rp, in, n, o, trace);
+      return;
+    }
+    set_device(ctx);
+    const size_t n_out = n * (trace ? (rp->N + 1) * rp->m : 1);
+    DevBuf di(ctx, n * sizeof(fe)), dout(ctx, n_out * sizeof(fe));
+    SG_HIP(hipMemcpyAsync(di.get(), in, n * sizeof(fe), hipMemcpyHostToDevice, ctx->stream));
+    rescue_batch_launch(ctx, *rp, di.as<fe>(), n, dout.as<fe>(), trace);
+    SG_HIP(hipMemcpyAsync(o, dout.get(), n_out * sizeof(fe), hipMemcpyDeviceToHost, ctx->stream));
+    host_wait(ctx, ctx->stream);
+  });
+}
+
+int rescue_batch_entry_dev(sg_ctx* ctx, const sg_rescue* rp, const sg_fe* d_inputs, size_t n, sg_fe* d_out,
+                           bool trace) {
+  return guard(ctx, [&] {
+    set_device(ctx);
+    SG_REQUIRE(rp && (!n || (d_inputs && d_out)), "null argument");
+    SG_REQUIRE(rp->capacity == 1, "Received wrong number of input elements");
+    SG_REQUIRE(rescue_has_kernel(*rp), "Rescue-Prime batch kernels exist for m = 2, 3, 4 (the host-pointer forms serve every m)");
+    if (!n) return;
+    rescue_batch_launch(ctx, *rp, reinterpret_cast<const fe*>(d_inputs), n, reinterpret_cast<fe*>(d_out), trace);
+    // async mode (sg_ctx_set_async): stream-ordered, the caller synchronizes
+    if (!ctx->async_dev) host_wait(ctx, ctx->stream);
+  });
 }
 
 // rescue_prime.rs:206-283
@@ -1816,6 +1977,25 @@ extern "C" int sg_rescue_trace(sg_ctx* ctx, const sg_rescue* rp, sg_fe input, sg
     std::vector<fe> t = rescue_trace(*rp, to_fe(input));
     memcpy(trace, t.data(), t.size() * sizeof(fe));
   });
+}
+
+extern "C" int sg_rescue_hash_batch(sg_ctx* ctx, const sg_rescue* rp, const sg_fe* inputs, size_t n, sg_fe* out) {
+  return rescue_batch_entry(ctx, rp, inputs, n, out, false);
+}
+
+extern "C" int sg_rescue_hash_batch_dev(sg_ctx* ctx, const sg_rescue* rp, const sg_fe* d_inputs, size_t n,
+                                        sg_fe* d_out) {
+  return rescue_batch_entry_dev(ctx, rp, d_inputs, n, d_out, false);
+}
+
+extern "C" int sg_rescue_trace_batch(sg_ctx* ctx, const sg_rescue* rp, const sg_fe* inputs, size_t n,
+                                     sg_fe* traces) {
+  return rescue_batch_entry(ctx, rp, inputs, n, traces, true);
+}
+
+extern "C" int sg_rescue_trace_batch_dev(sg_ctx* ctx, const sg_rescue* rp, const sg_fe* d_inputs, size_t n,
+                                         sg_fe* d_traces) {
+  return rescue_batch_entry_dev(ctx, rp, d_inputs, n, d_traces, true);
 }
 
 extern "C" int sg_rescue_transition_constraints(sg_ctx* ctx, const sg_rescue* rp, sg_fe omicron,

@@ -86,3 +86,8 @@ struct Stream {
 bool deserialize_stream(const uint8_t* b, size_t len, Stream& s, std::string& err);
 
 }  // namespace sg
+
+// the C ABI's native stream handle (stark_gpu.h sg_stream)
+struct sg_stream {
+  sg::Stream s;
+};

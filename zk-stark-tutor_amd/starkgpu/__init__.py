@@ -12,5 +12,6 @@ from .algebra import (Polynomial, evaluate_points, fast_coset_divide, fast_inter
                       fast_interpolate_geometric_dev, fast_multiply, fast_zerofier, fast_zerofier_geometric,
                       zerofier_geometric_at)
 from .stark import MPolynomial, RescuePrime, Stark
+from .rpsss import RPSSS
 
 __all__ = [n for n in dir() if not n.startswith("_")]

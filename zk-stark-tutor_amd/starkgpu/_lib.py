@@ -200,6 +200,18 @@ PROTOTYPES = {
     "sg_rescue_trace": (ctypes.c_int, [_vp, _vp, sg_fe, _vp]),
     "sg_rescue_transition_constraints": (ctypes.c_int, [_vp, _vp, sg_fe, ctypes.c_uint64, _P(_vp)]),
     "sg_rescue_boundary_constraints": (ctypes.c_int, [_vp, sg_fe, _vp]),
+    "sg_rescue_hash_batch": (ctypes.c_int, [_vp, _vp, _vp, _sz, _vp]),
+    "sg_rescue_hash_batch_dev": (ctypes.c_int, [_vp, _vp, _vp, _sz, _vp]),
+    "sg_rescue_trace_batch": (ctypes.c_int, [_vp, _vp, _vp, _sz, _vp]),
+    "sg_rescue_trace_batch_dev": (ctypes.c_int, [_vp, _vp, _vp, _sz, _vp]),
+    # RPSSS (rpsss.rs)
+    "sg_rpsss_create": (ctypes.c_int, [_vp, _sz, _sz, _sz, _sz, _P(_vp)]),
+    "sg_rpsss_free": (None, [_vp]),
+    "sg_rpsss_params": (ctypes.c_int, [_vp, _P(_sz), _P(_sz)]),
+    "sg_rpsss_keygen": (ctypes.c_int, [_vp, _vp, _vp, _fep, _fep]),
+    "sg_rpsss_keygen_batch": (ctypes.c_int, [_vp, _vp, _vp, _sz, _vp, _vp]),
+    "sg_rpsss_sign": (ctypes.c_int, [_vp, _vp, sg_fe, _vp, _sz, _vp, _vp, _sz, _P(_vp)]),
+    "sg_rpsss_verify": (ctypes.c_int, [_vp, _vp, sg_fe, _vp, _sz, _vp, _sz]),
     # STARK (stark/stark.rs)
     "sg_stark_create": (ctypes.c_int, [_vp, _sz, _sz, _sz, _sz, _sz, _sz, _P(_vp)]),
     "sg_stark_free": (None, [_vp]),

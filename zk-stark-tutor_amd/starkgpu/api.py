@@ -137,7 +137,9 @@ class Context:
     def set_option(self, name: str, value) -> None:
         """sg_ctx_set_option: "domain_cache", "air_generic", "geo_decimate", "lean_trees", "stream_pin",
         "world1_sharded", "lean_drop", "fri_gate", "verify_device" -- equivalent paths (same proof
-        bytes, same verdicts) that the tests compare."""
+        bytes, same verdicts) that the tests compare -- and "rescue_device_min": the batch size from
+        which RescuePrime.hash_batch / trace_batch and RPSSS.keygen_batch run on the device (default
+        the measured crossover; 0 = always the device; same values either way)."""
         self.check(self._lib.sg_ctx_set_option(self.handle, name.encode(), int(value)))
 
     @contextlib.contextmanager

@@ -163,6 +163,43 @@ class RescuePrime:
         self.ctx.check(self.ctx._lib.sg_rescue_trace(self.ctx.handle, self.handle, _fe(x), _ptr(t)))
         return t
 
+    def hash_batch(self, xs) -> List[int]:
+        """rescue_prime.rs:185-192 for every input (sg_rescue_hash_batch): one lane per input on the
+        device from the context option "rescue_device_min" on, a host loop below it, on a
+        HostContext and for an m without a kernel (m outside 2..4) -- the same values."""
+        x = fe_array(xs)
+        out = np.empty((max(len(x), 1), 2), dtype=np.uint64)
+        self.ctx.check(self.ctx._lib.sg_rescue_hash_batch(self.ctx.handle, self.handle, _ptr(x), len(x), _ptr(out)))
+        return to_ints(out[:len(x)])
+
+    def trace_batch_array(self, xs) -> np.ndarray:
+        """The traces of every input as an (n * (N+1) * m, 2) uint64 array: input i's trace is the
+        contiguous (N+1) x m block trace_array() returns (sg_rescue_trace_batch)."""
+        x = fe_array(xs)
+        per = (self.N + 1) * self.m
+        out = np.empty((max(len(x) * per, 1), 2), dtype=np.uint64)
+        self.ctx.check(self.ctx._lib.sg_rescue_trace_batch(self.ctx.handle, self.handle, _ptr(x), len(x), _ptr(out)))
+        return out[:len(x) * per]
+
+    def trace_batch(self, xs) -> List[List[List[int]]]:
+        """rescue_prime.rs:194-204 for every input: [input][row][register]."""
+        flat = to_ints(self.trace_batch_array(xs))
+        m, per = self.m, (self.N + 1) * self.m
+        return [[flat[i * per + r * m:i * per + (r + 1) * m] for r in range(self.N + 1)]
+                for i in range(len(flat) // per)]
+
+    def hash_batch_dev(self, d_inputs: int, n: int, d_out: int) -> None:
+        """hash_batch() over device memory (n inputs -> n outputs); m in 2..4."""
+        self.ctx.check(self.ctx._lib.sg_rescue_hash_batch_dev(self.ctx.handle, self.handle, ctypes.c_void_p(d_inputs),
+                                                              n, ctypes.c_void_p(d_out)))
+
+    def trace_batch_dev(self, d_inputs: int, n: int, d_traces: int) -> None:
+        """trace_batch() over device memory (n inputs -> n x (N+1) x m); block i is a valid d_trace
+        of Stark.prove_dev."""
+        self.ctx.check(self.ctx._lib.sg_rescue_trace_batch_dev(self.ctx.handle, self.handle,
+                                                               ctypes.c_void_p(d_inputs), n,
+                                                               ctypes.c_void_p(d_traces)))
+
     def transition_constraints(self, omicron: int, omicron_domain_length: int) -> List[MPolynomial]:
         out = (ctypes.c_void_p * self.m)()
         self.ctx.check(self.ctx._lib.sg_rescue_transition_constraints(self.ctx.handle, self.handle, _fe(omicron),
